@@ -32,6 +32,7 @@ import sys
 import threading
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -380,6 +381,31 @@ def emit(full):
     return line
 
 
+DUMP_LIMIT = 64 * 2 ** 20      # bytes: everything --dump-outputs writes, .npy headers included
+
+
+def dump_outputs(outdir, arrays, limit=DUMP_LIMIT, seed=0):
+    """--dump-outputs: write each array of `arrays` ({name: tensor}) as outdir/<name>.npy, float64 as float64 and anything else as float32.
+    When the arrays together exceed `limit`, each one is replaced by a fixed sample of its flattened elements: the first k positions of a
+    permutation seeded with `seed`, in ascending order, k its share of the limit.  The positions depend only on the array's size and `seed`, so
+    two builds run with the same arguments write files that compare element for element.  Returns {name: {"shape", "elements", "sampled"}}."""
+    os.makedirs(outdir, exist_ok=True)
+    arrays = {k: v.detach() if v.dtype == torch.float64 else v.detach().float() for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    budget = limit - 4096 * len(arrays)          # room for the .npy headers
+    info = {}
+    for name, v in arrays.items():
+        flat = v.reshape(-1)
+        n = flat.numel()
+        k = n if total <= budget else (n * budget) // total
+        if k < n:
+            pos = torch.randperm(n, generator=torch.Generator().manual_seed(seed))[:k].sort().values
+            flat = flat[pos.to(flat.device)]
+        np.save(os.path.join(outdir, name + ".npy"), flat.cpu().numpy() if k < n else v.cpu().numpy())
+        info[name] = {"shape": list(v.shape), "elements": k, "sampled": k < n}
+    return info
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -410,7 +436,11 @@ def main():
                          "needs to enqueue it — and at N = 1 when a probe step shows the host needing >= half of the step to enqueue it")
     ap.add_argument("--cpu-baseline-only", action="store_true", help="no GPU: time the reference module and the oracle port on window 0, write "
                                                                      "profiles/cpu_baseline_reference.json (run where /root/reference is mounted)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the composite of the headline's last timed step as "
+                                                          "DIR/composite.npy (float32; a fixed seeded sample of its elements when over 64 MB)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.cpu_baseline_only:
         return cpu_baseline_only(args)
 
@@ -766,6 +796,10 @@ def main():
     if rank == 0:
         headline_weak = world == 1 or args.scaling == "weak" or strong_res is None
         out = assemble(weak_res if headline_weak else strong_res, weak=headline_weak, strong_error=strong_err)
+        if args.dump_outputs:
+            # what ClipRunner.run() handed back in the headline's last timed step: comp [N, H, W, 3] fp32, 0..255 scale
+            info = dump_outputs(args.dump_outputs, {"composite": (weak_res if headline_weak else strong_res)["comp"]})
+            print(f"bench: outputs written to {args.dump_outputs}: {json.dumps(info)}", file=sys.stderr, flush=True)
         if pipe_sharded is not None:
             out["pipeline_sharded"] = pipe_sharded
         if world > 1:

@@ -133,8 +133,8 @@ def c2_spatial_mhsa(dev, model, prec, t=10, reps=5):
     f = torch.randn(t * th * tw, 256, generator=g).to(dev)
     fn = lambda: net._spatial_attention(x, f, P["s0"], t, th, tw)
     dt, _ = _timed(fn, reps=reps, warm=2)
-    # ... and as a captured hipGraph (inside a capture the module forks its value / key paths onto two more streams: a call this small is a
-    # dependency graph of under-filled launches, and enqueued eagerly it is bound by the host: profiles/r06_run6_*)
+    # ... and as a captured hipGraph (one stream: captures never fork, see FGT._spatial_attention; enqueued eagerly a call this small is bound
+    # by the host: profiles/r06_run6_*)
     from fgt_amd import fgt_model as _fm
     from fgt_amd.graph import GraphedCall
     variants = {}
@@ -166,7 +166,7 @@ def c2_spatial_mhsa(dev, model, prec, t=10, reps=5):
             "mfma_frac_linears": round(tf(cfl, cms) / peak, 4), "mfma_frac_attention_kernel": round(tf(afl, ams) / peak, 4),
             "hbm_frac_attention_kernel": round(aby / max(ams * 1e-3, 1e-12) / 1e9 / PEAK_HBM, 4),
             "launches": {"linear_gemm": cn, "attention": an}, "peak_tflops": peak,
-            "streams_in_graph_replay": 3 if 0 < t * th * tw <= _fm.SPATIAL_STREAM_ROWS else 1, **variants,
+            "streams_in_graph_replay": 1, **variants,
             **({"mfma_frac_module_wall_graph_replay": round(tf(cfl + afl, variants["graph_replay_ms"]) / peak, 4)} if "graph_replay_ms" in variants else {})}
 
 

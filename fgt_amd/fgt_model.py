@@ -29,10 +29,10 @@ SPLIT_ATTENTION = os.environ.get("FGT_SPLIT_ATTN", "1") != "0"
 FOLD_CONV = os.environ.get("FGT_FOLD_CONV", "1") != "0"
 # the encoder's 8-group layer packed as 4 groups with block-diagonal weights (FGT._pack_encoder_layer); 0: as the reference groups it (A/B)
 ENC_MERGE_GROUPS = os.environ.get("FGT_ENC_MERGE_GROUPS", "1") != "0"
-# SWMHSA on three HIP streams when a call is too small to fill the chip (see FGT._spatial_attention): at most this many token rows per call
+# SWMHSA on three HIP streams (eagerly, FGT_SPATIAL_STREAMS_EAGER=1) when a call is too small to fill the chip (see FGT._spatial_attention): at most this many token rows per call
 # (BASELINE config C2, t = 10: 7 200 rows; the benchmark's step batches 136 frames = 97 920 rows per call and stays on one stream).  0: never
 SPATIAL_STREAM_ROWS = int(os.environ.get("FGT_SPATIAL_STREAM_ROWS", "32768"))
-SPATIAL_STREAMS_EAGER = os.environ.get("FGT_SPATIAL_STREAMS_EAGER", "0") == "1"      # (tests / measurements: the three streams outside a capture too)
+SPATIAL_STREAMS_EAGER = os.environ.get("FGT_SPATIAL_STREAMS_EAGER", "0") == "1"      # (tests / measurements; never inside a stream capture)
 # tile order of the fold convolutions (fgt_conv_desc.tile_order): 1 = N-major inside an XCD (their 7 / 21 MB weight matrices do not fit the L2)
 FOLD_TILE_ORDER = int(os.environ.get("FGT_FOLD_TILE_ORDER", "1"))
 
@@ -569,14 +569,16 @@ class FGT(nn.Module):
         osp = "only" if (sc and SPLIT_ATTENTION) else None
         # The module is a small dependency graph, not a chain: the value path (global-token pool of x, three LayerNorms, the v Linear) needs neither
         # the flow re-weighting nor the q / k path, and the k path parts from the q path behind the shared LayerNorm.  A call that cannot fill the
-        # chip by itself (BASELINE config C2: 7 200 token rows = 224 tiles per 512-wide GEMM on 256 CUs x 2 workgroups) therefore runs on THREE
+        # chip by itself (BASELINE config C2: 7 200 token rows = 224 tiles per 512-wide GEMM on 256 CUs x 2 workgroups) can run on THREE
         # HIP streams — main: re-weighting -> LN(q|k) -> q -> attention -> out-projection; k: global-token pool of [x | f w] -> LN -> k;
         # v: the value path — so the under-filled launches share the chip (14 launches deep becomes 5).  Same kernels on the same data: bit-identical
-        # to the single-stream order (tests/test_fgt_gpu.py); capturable (fork / join on the capturing stream).  Large calls (the clip runner's
-        # 136-frame batches) fill the chip per launch and stay on one stream.
-        # Only inside a stream capture: enqueued eagerly the module is bound by the host (15 launches + 6 cross-stream waits at 5-10 us each:
-        # 0.38 ms on three streams against 0.30 on one, profiles/r06_run6_*), as a replayed graph by the GPU (0.26 -> 0.22 ms).
-        par = x.is_cuda and 0 < R <= SPATIAL_STREAM_ROWS and (SPATIAL_STREAMS_EAGER or torch.cuda.is_current_stream_capturing())
+        # to the single-stream order (tests/test_fgt_gpu.py).  Large calls (the clip runner's 136-frame batches) fill the chip per launch.
+        # Eagerly only, and only on request (FGT_SPATIAL_STREAMS_EAGER=1): enqueued eagerly the module is bound by the host (15 launches + 6
+        # cross-stream waits at 5-10 us each: 0.38 ms on three streams against 0.30 on one, profiles/r06_run6_*).  Never inside a stream capture:
+        # a captured graph with fork / join branches crashes the host in its first replay (SIGSEGV in hipGraphLaunch) on the HIP runtime torch
+        # ships, while single-stream graphs of hundreds of launches replay correctly — captured graphs stay on one stream (0.26 ms per C2 module
+        # replayed, against 0.22 with the fork where it replayed).
+        par = x.is_cuda and 0 < R <= SPATIAL_STREAM_ROWS and SPATIAL_STREAMS_EAGER and not torch.cuda.is_current_stream_capturing()
         if par:
             main = torch.cuda.current_stream()
             s_k, s_v = self._side_streams(dev)

@@ -157,7 +157,8 @@ def test_config2_spatial_block_t10_order_one_tokens(prec, blk_tol, att_tol, dev,
 @pytest.mark.parametrize("prec", ["fp32", "bf16x3"])
 def test_config2_spatial_mhsa_three_streams_equal_one_stream_and_graph_replay(prec, dev, monkeypatch):
     """The C2-sized SWMHSA call runs its value / key / query paths on three HIP streams (fgt_model.SPATIAL_STREAM_ROWS): the same kernels on
-    the same data — bit-identical to the single-stream order, repeatably (20 calls), and as a captured hipGraph (fork / join inside the capture)."""
+    the same data — bit-identical to the single-stream order, repeatably (20 calls), and as a captured hipGraph (captures never fork: a graph
+    with fork / join branches crashed the host in its first replay)."""
     from fgt_amd import fgt_model, ops
     from fgt_amd.graph import GraphedCall
     monkeypatch.setattr(ops, "DEFAULT_CONV_PRECISION", prec)
